@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: achieved FP8 TFLOPS of ``fp8_gemm_nt`` at M=4096 N=4096 K=7168 (BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload dense|contiguous|masked|c3_{nt,nn,tn,tt}|wgrad|wgrad_ksplit|kgrouped|dense_ue8m0|dense_sm100|masked_ue8m0|dgrad_ktail|dgrad_ksplit|decode_m1|decode_m1_long|expert_mlp|expert_mlp_unfused|dense_sfa_rowmajor|dgrad_ktail_ue8m0|dense_m128|c3_nn_ue8m0|contiguous_ue8m0|dense_ue8m0_g32|wgrad_ue8m0|kgrouped_ue8m0|kgrouped_ue8m0_g32|decode_m1_ue8m0]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--workload dense|contiguous|masked|c3_{nt,nn,tn,tt}|wgrad|wgrad_ksplit|kgrouped|dense_ue8m0|dense_sm100|masked_ue8m0|dgrad_ktail|dgrad_ksplit|decode_m1|decode_m1_long|expert_mlp|expert_mlp_unfused|dense_sfa_rowmajor|dgrad_ktail_ue8m0|dense_m128|c3_nn_ue8m0|contiguous_ue8m0|dense_ue8m0_g32|wgrad_ue8m0|kgrouped_ue8m0|kgrouped_ue8m0_g32|decode_m1_ue8m0]
 
 A "step" is one pass of the hot path (one operator call) over one batch of synthetic, already HBM-resident input
 (``torch.manual_seed`` BF16 randn, quantised with the reference's per-token / per-block casts).  Input sets are
@@ -14,6 +14,8 @@ dense FP8 MFMA peak or the HBM peak, timed with HIP events on the launch stream)
 CPU-runnable test expression timed on the host cores of this box) and, on the default run, ``secondary``: the same
 measurement, shortened, for the other BASELINE configurations (C3 per layout, C4, C5), the wgrad recipe, the K-grouped
 GEMM, the packed-UE8M0 forms of C2 and C5 and two dgrad entries of the reference sweep (K tail, K split).
+``--dump-outputs DIR`` writes what the last timed step handed its caller as ``DIR/<name>.npy`` (float32, at most 64 MB: past that a
+fixed, seeded sample of rows), so that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import json
@@ -84,10 +86,13 @@ def parse_args():
     ap.add_argument('--sets', type=int, default=4, help='rotating input sets (defeats Infinity-Cache residency)')
     ap.add_argument('--ep-capacity', type=int, default=0,
                     help='masked workload with --gpus > 1: rows per (rank, expert) block of the fixed-shape exchange (0 = exact split sizes)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy (float32; a fixed, seeded sample of rows '
+                         'past 64 MB in all)')
     return ap.parse_args()
 
 
-def make_ep_workload(sets: int, world: int, rank: int, phase_events: list, capacity: int = 0):
+def make_ep_workload(sets: int, world: int, rank: int, phase_events: list, capacity: int = 0, outputs=None):
     """BASELINE configs[4] across ranks: 8 experts per rank (8 * world in total, weights resident on their owner), 48
     token rows per rank routed to top-8 experts => about 48 rows per expert; one step = all-to-all dispatch + local masked
     grouped GEMM + all-to-all combine + top-k weighted reduce on the token's owner (deepgemm_amd/ep.py)."""
@@ -105,9 +110,14 @@ def make_ep_workload(sets: int, world: int, rank: int, phase_events: list, capac
         x = per_token_cast_to_fp8(torch.randn((tokens, k), dtype=torch.bfloat16, device='cuda'), use_ue8m0=False)
         ids = torch.stack([torch.randperm(num_experts, device='cuda')[:top_k] for _ in range(tokens)])
         weights = torch.softmax(torch.randn((tokens, top_k), device='cuda'), dim=-1)
-        calls.append(lambda x=x, ids=ids, weights=weights: ep.ep_m_grouped_fp8_gemm_nt_masked(
-            x, ids, b_local, num_experts, max_m, expected_m=48, topk_weights=weights, phase_events=phase_events,
-            capacity=capacity if capacity > 0 else None))
+        returned = {}                       # the combined rows the call returns (a fresh tensor each call)
+
+        def call(x=x, ids=ids, weights=weights, returned=returned):
+            returned['y'] = ep.ep_m_grouped_fp8_gemm_nt_masked(x, ids, b_local, num_experts, max_m, expected_m=48, topk_weights=weights,
+                                                               phase_events=phase_events, capacity=capacity if capacity > 0 else None)
+        calls.append(call)
+        if outputs is not None:
+            outputs.append(([], lambda returned=returned: dict(returned)))
     flops = 2.0 * tokens * top_k * n * k
     nbytes = float(b_local[0].numel() + 4 * b_local[1].numel() + tokens * top_k * (k + 4 * k // 128 + 2 * n))
     desc = {'workload': f'EP m_grouped_fp8_gemm_nt_masked: {num_experts} experts / {world} GPUs ({per_rank} per rank), about 48 rows per expert, '
@@ -117,12 +127,14 @@ def make_ep_workload(sets: int, world: int, rank: int, phase_events: list, capac
     return calls, flops, nbytes, desc, lambda: float('nan'), 'hbm'
 
 
-def make_workload(name: str, sets: int, world: int = 1, rank: int = 0, phase_events=None, ep_capacity: int = 0):
-    """Returns (zero-arg callables, flops per step, algorithmic bytes per step, description, checker, roofline bound)."""
+def make_workload(name: str, sets: int, world: int = 1, rank: int = 0, phase_events=None, ep_capacity: int = 0, outputs=None):
+    """Returns (zero-arg callables, flops per step, algorithmic bytes per step, description, checker, roofline bound).
+    `outputs`, if a list, receives one (buffers, view) pair per callable: the tensors the call writes and a zero-arg function returning
+    {name: tensor}, what the call hands its caller (masked / contiguous layouts: only the rows the call defines)."""
     calls, cases = [], []
     bound = 'mfma'
     if name == 'masked' and world > 1:
-        return make_ep_workload(sets, world, rank, phase_events, ep_capacity)
+        return make_ep_workload(sets, world, rank, phase_events, ep_capacity, outputs)
     if name == 'dense_sm100':
         # C2 as an SM100-style caller sends it: FP32 power-of-two scales (per_token / per_block casts with use_ue8m0=True, row-major
         # SFA as the cast returns it), scaling-factor mode 'sm100' -- the WHOLE call: the cast branch's pack launches (SFA; SFB with the
@@ -430,7 +442,45 @@ def make_workload(name: str, sets: int, world: int = 1, rank: int = 0, phase_eve
         def check():
             c = cases[0]
             return max(calc_diff(c.d[g, :int(r)], c.ref_d[g, :int(r)]) for g, r in enumerate(c.masked_m.tolist()) if r)
+    if outputs is not None:
+        outputs.extend(case_outputs(name, c) for c in cases)
     return calls, flops, float(nbytes), desc, check, bound
+
+
+def _masked_rows(d: torch.Tensor, masked_m: torch.Tensor) -> torch.Tensor:
+    return torch.cat([d[g, :r] for g, r in enumerate(masked_m.tolist())])
+
+
+def case_outputs(name: str, case):
+    """(buffers, view) of one input set of `make_workload` (see there)."""
+    if name.startswith('expert_mlp'):
+        y, masked = case[1], case[2]
+        return [y], lambda: {'y': _masked_rows(y, masked)}
+    if name.startswith('masked'):
+        return [case.d], lambda: {'d': _masked_rows(case.d, case.masked_m)}
+    if name.startswith('contiguous'):               # alignment-padding rows (grouped_layout -1) belong to no group
+        return [case.d], lambda: {'d': case.d[case.grouped_layout >= 0]}
+    return [case.d], lambda: {'d': case.d}
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """Write `arrays` as directory/<name>.npy in float32.  Past DUMP_LIMIT_BYTES in all, each array is cut to its share of the limit: a
+    fixed, seeded sample of its rows (last dimension kept whole) in row order, saved as [rows, last dim] -- the same rows on every run."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if total > DUMP_LIMIT_BYTES and t.dim() > 0:
+            rows = t.reshape(-1, t.size(-1))
+            keep = max(1, int(DUMP_LIMIT_BYTES * 4 * t.numel() / total) // (4 * rows.size(1)))
+            if keep < rows.size(0):
+                pick = torch.randperm(rows.size(0), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+                t = rows[pick.to(rows.device)]
+        np.save(os.path.join(directory, f'{name}.npy'), t.cpu().numpy())
 
 
 def roofline_record(flops: float, nbytes: float, kernel_s: float, bound: str, kernel: str, counters=None, useful_flops=None, recipe_roof=None):
@@ -562,7 +612,11 @@ def run(rank: int, world: int, local_rank: int, args):
 
     dg.set_forced_config(args.config)
     phase_events = []
-    calls, flops, nbytes, desc, check, bound = make_workload(args.workload, args.sets, world, rank, phase_events, args.ep_capacity)
+    outputs = [] if args.dump_outputs else None
+    calls, flops, nbytes, desc, check, bound = make_workload(args.workload, args.sets, world, rank, phase_events, args.ep_capacity, outputs)
+    # --dump-outputs: the written buffers as generated, put back before the timed steps, so that what the last step computes does not depend
+    # on how many calls the time-bounded warm-up made (the FP32 accumulate workloads add into D in place)
+    initial = [[t.clone() for t in buffers] for buffers, _ in outputs] if outputs is not None else None
 
     calls[0]()
     torch.cuda.synchronize()
@@ -581,6 +635,11 @@ def run(rank: int, world: int, local_rank: int, args):
         calls[i % len(calls)]()
     torch.cuda.synchronize()
     phase_events.clear()
+    if initial is not None:
+        for (buffers, _), saved in zip(outputs, initial):
+            for t, t0 in zip(buffers, saved):
+                t.copy_(t0)
+        initial = None
 
     start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     if distributed:
@@ -609,6 +668,10 @@ def run(rank: int, world: int, local_rank: int, args):
         if split is not None:
             split = [float(x) for x in t[1:].tolist()]
     kernel_s = start.elapsed_time(end) / 1e3 / args.steps       # average launch duration of the dominant kernel (EP: of the whole step)
+    if outputs is not None:                 # what the last timed step handed its caller
+        arrays = outputs[(args.steps - 1) % len(calls)][1]()
+        dump_outputs(args.dump_outputs, {(f'{k}_rank{rank}' if distributed else k): v for k, v in arrays.items()})
+        arrays = outputs = None
 
     if rank == 0:
         total_flops = flops * args.steps * world
