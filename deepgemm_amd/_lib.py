@@ -49,6 +49,11 @@ SIGNATURES = {
     'dg_per_token_cast_to_fp8': (_i32, [_vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp]),
     'dg_block_cast_to_fp8': (_i32, [_vp, _vp, _vp, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _vp]),
     'dg_transpose_fp8': (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _vp]),
+    'dg_bf16_gemm_nt': (_i32, [_vp] * 3 + [_i32] * 3 + [_i64] * 3 + [_i32, _i32, _vp, _i64, _vp]),
+    'dg_m_grouped_bf16_gemm_nt_contiguous': (_i32, [_vp] * 4 + [_i32] * 4 + [_i64] * 4 + [_i32, _i32, _vp]),
+    'dg_m_grouped_bf16_gemm_nt_masked': (_i32, [_vp] * 4 + [_i32] * 5 + [_i64] * 6 + [_vp]),
+    'dg_transpose_bf16': (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _vp]),
+    'dg_bf16_select_config': (_cp, [_i32] * 8),
     'dg_set_num_cus': (_i32, [_i32]),
     'dg_get_num_cus': (_i32, []),
     'dg_set_forced_config': (_i32, [_cp]),

@@ -15,6 +15,7 @@
 #include "fp8_gemm_kernels.hpp"
 #include "fp8_gemm_quad.hpp"
 #include "fp8_gemm_moe.hpp"
+#include "bf16_gemm_kernels.hpp"
 #ifndef DG_MONOLITHIC   // (the default build: the template kernels are compiled by the dg_shard.hip units, see kernel_instances.inc)
 namespace dg {
 #define DG_HAVE_MOE_HPP 1
@@ -40,9 +41,21 @@ std::atomic<long long*> g_debug_buffer{nullptr};
 std::mutex g_forced_config_mutex;
 std::string g_forced_config = "auto";              // guarded by g_forced_config_mutex
 
-std::string forced_config() {
+std::string forced_name() {
     std::lock_guard<std::mutex> lock(g_forced_config_mutex);
     return g_forced_config;
+}
+
+// One forced name for both families (set_forced_config): a BF16 name (prefix bf16_) forces the BF16 entries only -- the FP8 selection
+// sees "auto" -- and an FP8 name the FP8 entries only.
+bool is_bf16_config_name(const std::string& name) { return name.compare(0, 5, "bf16_") == 0; }
+std::string forced_config() {
+    std::string name = forced_name();
+    return is_bf16_config_name(name) ? std::string("auto") : name;
+}
+std::string forced_bf16_config() {
+    std::string name = forced_name();
+    return is_bf16_config_name(name) ? name : std::string("auto");
 }
 
 int fail(const char* file, int line, const char* what) {
@@ -1426,6 +1439,138 @@ int launch_e8(dg::GemmParams& p, int expected_m, void* stream, int gran_k = 128)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// BF16 GEMMs (bf16_gemm_kernels.hpp).  Selection from the shape and the CU count only:
+//   dense m <= 64 / masked expected_m <= 64: the 64 x 32 weight-streaming tile; a dense problem whose tiles fill at most half of the CUs is
+//     cut along K into pieces (FP32 partials in the caller's workspace + dg_bf16_split_k_sum_kernel) when the caller passes a workspace;
+//   everything else: the 256 x 256 tile, except the psum layout and contiguous alignments that 256 neither divides nor halves (128 x 256,
+//     then the 64-row tile).
+// ---------------------------------------------------------------------------------------------------------------------
+struct Bf16Config { const char* name; KernelFn fn; int bm, bn, threads; int per_cu; bool ksplit; };
+const Bf16Config kBf16Configs[] = {
+    {"bf16_256x256", dg::dg_bf16_gemm_kernel<256, 256, 2, 4, 2>, 256, 256, 512, 1, false},
+    {"bf16_128x256", dg::dg_bf16_gemm_kernel<128, 256, 2, 4, 3>, 128, 256, 512, 1, false},
+    {"bf16_stream_64x32", dg::dg_bf16_gemm_kernel<64, 32, 4, 1, 8>, 64, 32, 256, 1, false},
+    {"bf16_stream_ks_64x32", dg::dg_bf16_gemm_kernel<64, 32, 4, 1, 8, true>, 64, 32, 256, 1, true},
+};
+constexpr int kBf16SmallM = 64;
+
+const Bf16Config* bf16_config_by_name(const std::string& name) {
+    for (const Bf16Config& c : kBf16Configs)
+        if (name == c.name)
+            return &c;
+    return nullptr;
+}
+
+// K pieces of the dense small-M tile: as many as keep tiles x pieces within one round over the CUs, at most 8, at least 8 K blocks each;
+// 1 = no split (the tiles fill more than half the chip, or the workspace cannot hold the FP32 partials)
+int bf16_split_pieces(const dg::GemmParams& p, size_t workspace_bytes) {
+    if (p.gemm_type != dg::kNormal || p.m > kBf16SmallM)
+        return 1;
+    const long tiles = static_cast<long>(ceil_div(p.m, 64)) * ceil_div(p.n, 32);
+    long pieces = std::min<long>(std::min<long>(8, num_cus() / std::max<long>(tiles, 1)), ceil_div(p.k, 64) / 8);
+    if (pieces < 2 || static_cast<size_t>(pieces) * p.m * p.n * sizeof(float) > workspace_bytes)
+        return 1;
+    return static_cast<int>(pieces);
+}
+
+// The automatic choice (forced names are resolved by the caller); nullptr = no BF16 kernel takes this contiguous alignment.
+const Bf16Config* select_bf16_config(const dg::GemmParams& p, int expected_m, size_t workspace_bytes) {
+    switch (p.gemm_type) {
+        case dg::kNormal:
+            if (p.m <= kBf16SmallM)
+                return bf16_config_by_name(bf16_split_pieces(p, workspace_bytes) >= 2 ? "bf16_stream_ks_64x32" : "bf16_stream_64x32");
+            return bf16_config_by_name("bf16_256x256");
+        case dg::kMasked:
+            return bf16_config_by_name((expected_m > 0 ? expected_m : p.m) <= kBf16SmallM ? "bf16_stream_64x32" : "bf16_256x256");
+        case dg::kContiguous:
+            if (p.m_alignment % 256 == 0 || p.m_alignment == 128)
+                return bf16_config_by_name("bf16_256x256");       // (alignment 128: tiles of two halves, walked twice where two groups meet)
+            [[fallthrough]];
+        default:                                                  // kContiguousPsum: a tile must not straddle two groups
+            if (p.m_alignment % 128 == 0)
+                return bf16_config_by_name("bf16_128x256");
+            return p.m_alignment % 64 == 0 ? bf16_config_by_name("bf16_stream_64x32") : nullptr;
+    }
+}
+
+int launch_bf16(dg::GemmParams& p, int expected_m, void* workspace, size_t workspace_bytes, void* stream) {
+    const std::string forced = forced_bf16_config();
+    const Bf16Config* cfg = forced == "auto" ? select_bf16_config(p, expected_m, workspace != nullptr ? workspace_bytes : 0)
+                                             : bf16_config_by_name(forced);
+    if (cfg == nullptr) {
+        g_last_error = forced == "auto" ? "no BF16 kernel configuration takes a contiguous-layout M alignment that is not a multiple of 64"
+                                        : "unknown BF16 kernel configuration '" + forced + "'";
+        return 3;
+    }
+    if (p.gemm_type == dg::kContiguous || p.gemm_type == dg::kContiguousPsum) {
+        const bool divides = p.m_alignment % cfg->bm == 0;
+        const bool halves = p.gemm_type == dg::kContiguous && cfg->bm == 2 * p.m_alignment;
+        if (!divides && !halves) {
+            g_last_error = std::string("config '") + cfg->name + "' does not divide the contiguous-layout M alignment";
+            return 3;
+        }
+    }
+    if (cfg->ksplit && p.gemm_type != dg::kNormal) {
+        g_last_error = std::string("config '") + cfg->name + "' implements dense problems only";
+        return 3;
+    }
+    // K pieces: the automatic rule's, or four (at most one per K block, at least two) for the form forced by name
+    const int pieces = !cfg->ksplit ? 1 : forced == "auto" ? bf16_split_pieces(p, workspace_bytes) : std::max(2, std::min(4, ceil_div(p.k, 64)));
+    if (cfg->ksplit && (workspace == nullptr || static_cast<size_t>(pieces) * p.m * p.n * sizeof(float) > workspace_bytes)) {
+        g_last_error = std::string("config '") + cfg->name + "' needs a workspace of pieces x m x n FP32 values";
+        return 3;
+    }
+    g_last_config = cfg->name;
+    p.num_m_tiles = ceil_div(p.m, cfg->bm);
+    p.num_n_tiles = ceil_div(p.n, cfg->bn);
+    p.group_m = p.num_m_tiles >= 8 ? 4 : (p.num_m_tiles >= 2 ? 2 : 1);
+    const size_t elem = p.d_dtype == DG_BF16 ? 2 : 4;
+    p.d_vec_ok = aligned16(p.d) && (p.d_sm * elem) % 16 == 0 && (p.d_sg * elem) % 16 == 0;
+    p.d_nt = output_streams_past_l2(p);
+    const long total = static_cast<long>(p.num_m_tiles) * p.num_n_tiles;
+    long grid = total;
+    if (p.gemm_type == dg::kMasked)
+        grid = std::min<long>(total * p.num_groups, static_cast<long>(num_cus()) * cfg->per_cu);
+    if (grid <= 0)
+        return 0;
+    if (grid > 0x7fffffffL)
+        return fail(__FILE__, __LINE__, "grid too large");
+    if (cfg->ksplit) {
+        // the K pieces as work items writing FP32 partial tiles into the workspace ([pieces][m][n]), then the summing launch into D
+        const int f = pieces;
+        dg::GemmParams part = p;
+        part.d = workspace;
+        part.d_dtype = DG_FP32;
+        part.accumulate = 0;
+        part.d_sm = p.n;
+        part.d_sg = static_cast<int64_t>(p.m) * p.n;
+        part.d_vec_ok = p.n % 4 == 0;
+        part.d_nt = 0;
+        part.sk_factor = f;
+        hipLaunchKernelGGL(cfg->fn, dim3(static_cast<unsigned>(total * f)), dim3(cfg->threads), 0, static_cast<hipStream_t>(stream), part);
+        DG_HIP_CHECK(hipGetLastError());
+        const long items = (static_cast<long>(p.m) * p.n) / (p.n % 4 == 0 ? 4 : 1);
+        const unsigned sum_grid = static_cast<unsigned>(std::max<long>(1, std::min<long>((items + 255) / 256, 4L * num_cus())));
+        hipLaunchKernelGGL(dg::dg_bf16_split_k_sum_kernel, dim3(sum_grid), dim3(256), 0, static_cast<hipStream_t>(stream),
+                           static_cast<const float*>(workspace), f, p.m, p.n, p.d, static_cast<int64_t>(p.d_sm), p.d_dtype, p.accumulate);
+        DG_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    hipLaunchKernelGGL(cfg->fn, dim3(static_cast<unsigned>(grid)), dim3(cfg->threads), 0, static_cast<hipStream_t>(stream), p);
+    DG_HIP_CHECK(hipGetLastError());
+    if (env_knobs().print_configs)
+        fprintf(stderr, "[deepgemm_amd] bf16 type=%d m=%d n=%d k=%d groups=%d -> %s grid=%ld\n", p.gemm_type, p.m, p.n, p.k, p.num_groups,
+                cfg->name, grid);
+    return 0;
+}
+
+// Operand rows of a BF16 launch: K-major, 16-byte aligned (row strides multiples of 8 elements), k a multiple of 8, and a tile's rows
+// within reach of the LDS-DMA's 32-bit offsets.
+bool bf16_operand_ok(const void* ptr, int64_t row_stride, int64_t group_stride = 0) {
+    return aligned16(ptr) && row_stride % 8 == 0 && group_stride % 8 == 0 && row_stride * 2 * 256 < (1LL << 31);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2586,6 +2731,102 @@ int dg_transpose_fp8(const void* src, void* dst, int batches, int rows, int cols
     return 0;
 }
 
+int dg_bf16_gemm_nt(const void* a, const void* b, void* d, int m, int n, int k, int64_t a_stride_m, int64_t b_stride_n,
+                    int64_t d_stride_m, int d_dtype, int accumulate, void* workspace, int64_t workspace_bytes, void* stream) {
+    DG_CHECK(m >= 0 && n >= 0 && k >= 0);
+    if (m == 0 || n == 0)
+        return 0;
+    DG_CHECK(k > 0);   // k == 0 is resolved by the caller (D = C or 0) without a kernel, as in the reference
+    DG_CHECK(a != nullptr && b != nullptr && d != nullptr);
+    DG_CHECK(k % 8 == 0);
+    DG_CHECK(bf16_operand_ok(a, a_stride_m) && bf16_operand_ok(b, b_stride_n));
+    DG_CHECK(a_stride_m >= k && b_stride_n >= k);
+    DG_CHECK(d_dtype == DG_BF16 || d_dtype == DG_FP32);
+    DG_CHECK(d_stride_m >= n);
+    DG_CHECK(workspace == nullptr || (aligned16(workspace) && workspace_bytes >= 0));
+    dg::GemmParams p{};
+    p.a = static_cast<const uint8_t*>(a); p.b = static_cast<const uint8_t*>(b); p.d = d;
+    p.m = m; p.n = n; p.k = k; p.num_groups = 1;
+    p.a_sm = a_stride_m * 2; p.a_sk = 1; p.b_sn = b_stride_n * 2; p.b_sk = 1;       // (BF16 launches: operand strides in bytes)
+    p.d_sm = d_stride_m;
+    p.d_dtype = d_dtype; p.accumulate = accumulate ? 1 : 0;
+    p.gemm_type = dg::kNormal;
+    return launch_bf16(p, 0, workspace, workspace != nullptr ? static_cast<size_t>(workspace_bytes) : 0, stream);
+}
+
+int dg_m_grouped_bf16_gemm_nt_contiguous(const void* a, const void* b, void* d, const int32_t* grouped_layout, int num_groups,
+                                         int m, int n, int k, int64_t a_stride_m, int64_t b_stride_g, int64_t b_stride_n,
+                                         int64_t d_stride_m, int use_psum, int m_alignment, void* stream) {
+    DG_CHECK(m >= 0 && n > 0 && k > 0 && num_groups > 0);
+    if (m == 0)
+        return 0;
+    DG_CHECK(a != nullptr && b != nullptr && d != nullptr && grouped_layout != nullptr);
+    DG_CHECK(k % 8 == 0);
+    DG_CHECK(bf16_operand_ok(a, a_stride_m) && bf16_operand_ok(b, b_stride_n, b_stride_g));
+    DG_CHECK(a_stride_m >= k && b_stride_n >= k);
+    DG_CHECK(m_alignment > 0 && m_alignment % 16 == 0);
+    DG_CHECK(d_stride_m >= n);
+    dg::GemmParams p{};
+    p.a = static_cast<const uint8_t*>(a); p.b = static_cast<const uint8_t*>(b); p.d = d;
+    p.layout = grouped_layout;
+    p.m = m; p.n = n; p.k = k; p.num_groups = num_groups;
+    p.a_sm = a_stride_m * 2; p.a_sk = 1; p.b_sg = b_stride_g * 2; p.b_sn = b_stride_n * 2; p.b_sk = 1;
+    p.d_sm = d_stride_m;
+    p.d_dtype = DG_BF16; p.accumulate = 0;
+    p.gemm_type = use_psum ? dg::kContiguousPsum : dg::kContiguous;
+    p.m_alignment = m_alignment;
+    return launch_bf16(p, 0, nullptr, 0, stream);
+}
+
+int dg_m_grouped_bf16_gemm_nt_masked(const void* a, const void* b, void* d, const int32_t* masked_m, int num_groups, int m_max, int n,
+                                     int k, int expected_m, int64_t a_stride_g, int64_t a_stride_m, int64_t b_stride_g, int64_t b_stride_n,
+                                     int64_t d_stride_g, int64_t d_stride_m, void* stream) {
+    DG_CHECK(expected_m > 0 && m_max > 0 && n > 0 && k > 0 && num_groups > 0);
+    DG_CHECK(a != nullptr && b != nullptr && d != nullptr && masked_m != nullptr);
+    DG_CHECK(k % 8 == 0);
+    DG_CHECK(bf16_operand_ok(a, a_stride_m, a_stride_g) && bf16_operand_ok(b, b_stride_n, b_stride_g));
+    DG_CHECK(a_stride_m >= k && b_stride_n >= k);
+    DG_CHECK(d_stride_m >= n);
+    dg::GemmParams p{};
+    p.a = static_cast<const uint8_t*>(a); p.b = static_cast<const uint8_t*>(b); p.d = d;
+    p.layout = masked_m;
+    p.m = m_max; p.n = n; p.k = k; p.num_groups = num_groups;
+    p.a_sg = a_stride_g * 2; p.a_sm = a_stride_m * 2; p.a_sk = 1;
+    p.b_sg = b_stride_g * 2; p.b_sn = b_stride_n * 2; p.b_sk = 1;
+    p.d_sg = d_stride_g; p.d_sm = d_stride_m;
+    p.d_dtype = DG_BF16; p.accumulate = 0;
+    p.gemm_type = dg::kMasked;
+    return launch_bf16(p, expected_m < m_max ? expected_m : m_max, nullptr, 0, stream);
+}
+
+int dg_transpose_bf16(const void* src, void* dst, int batches, int rows, int cols,
+                      int64_t src_ld, int64_t dst_ld, int64_t src_batch_stride, int64_t dst_batch_stride, void* stream) {
+    DG_CHECK(batches >= 0 && rows >= 0 && cols >= 0);
+    if (batches == 0 || rows == 0 || cols == 0)
+        return 0;
+    DG_CHECK(src != nullptr && dst != nullptr && src != dst);
+    DG_CHECK(src_ld >= cols && dst_ld >= rows);
+    DG_CHECK(batches <= 65535 && (rows + 63) / 64 <= 65535);
+    const dim3 grid((cols + 63) / 64, (rows + 63) / 64, batches);
+    hipLaunchKernelGGL(dg::dg_transpose_bf16_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint16_t*>(src), static_cast<uint16_t*>(dst), rows, cols, src_ld, dst_ld,
+                       src_batch_stride, dst_batch_stride);
+    DG_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+const char* dg_bf16_select_config(int gemm_type, int m, int n, int k, int num_groups, int expected_m, int m_alignment, int has_workspace) {
+    // the BF16 kernel the automatic selection would launch for this shape (K-major, 16-byte aligned operands); nothing is launched and no
+    // device is needed (256 CUs are assumed when none is visible).  has_workspace: the caller would pass one of dg_split_k_workspace_bytes().
+    static thread_local std::string name;
+    dg::GemmParams p{};
+    p.m = m; p.n = n; p.k = k; p.num_groups = num_groups > 0 ? num_groups : 1;
+    p.gemm_type = gemm_type; p.m_alignment = m_alignment;
+    const Bf16Config* cfg = select_bf16_config(p, expected_m, has_workspace ? static_cast<size_t>(dg_split_k_workspace_bytes()) : 0);
+    name = cfg != nullptr ? cfg->name : "";
+    return name.c_str();
+}
+
 int dg_set_num_cus(int n) {
     if (n < 0)
         return fail(__FILE__, __LINE__, "num_cus >= 0");
@@ -2606,6 +2847,7 @@ int dg_set_forced_config(const char* name) {
             known = known || std::strcmp(name, kConfigs[i].name) == 0;
         for (const E8Config& c : kE8Configs)
             known = known || std::strcmp(name, c.name) == 0;
+        known = known || bf16_config_by_name(name) != nullptr;
         if (!known) {
             g_last_error = std::string("unknown kernel configuration '") + name + "'";
             return 1;
@@ -2628,13 +2870,15 @@ const char* dg_list_configs(void) {
             joined += std::string(i ? "," : "") + kConfigs[i].name;
         for (const E8Config& c : kE8Configs)
             joined += std::string(",") + c.name;
+        for (const Bf16Config& c : kBf16Configs)
+            joined += std::string(",") + c.name;
     }
     return joined.c_str();
 }
 
 const char* dg_get_forced_config(void) {
     thread_local std::string copy;
-    copy = forced_config();
+    copy = forced_name();
     return copy.c_str();
 }
 

@@ -110,4 +110,10 @@ DG_KERNEL_INSTANCE(void dg_fp8_gemm_quad_e8_kernel<128, 256, 0, false, 2, false,
 DG_KERNEL_INSTANCE(void dg_fp8_gemm_quad_e8_kernel<256, 256, 0, false, 2, false, 0, false, false, true, true>(DG_P))
 DG_KERNEL_INSTANCE(void dg_fp8_gemm_quad_e8_kernel<256, 256, 0, false, 2, false, 0, false, true, true, true>(DG_P))
 #endif
+#if !defined(DG_SHARD) || DG_SHARD == 10       // BF16 tiles (bf16_gemm_kernels.hpp)
+DG_KERNEL_INSTANCE(void dg_bf16_gemm_kernel<256, 256, 2, 4, 2>(DG_P))
+DG_KERNEL_INSTANCE(void dg_bf16_gemm_kernel<128, 256, 2, 4, 3>(DG_P))
+DG_KERNEL_INSTANCE(void dg_bf16_gemm_kernel<64, 32, 4, 1, 8>(DG_P))
+DG_KERNEL_INSTANCE(void dg_bf16_gemm_kernel<64, 32, 4, 1, 8, true>(DG_P))
+#endif
 #undef DG_P

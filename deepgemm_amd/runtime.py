@@ -93,6 +93,8 @@ def set_forced_config(name: str) -> None:
     gemm._VALIDATED_DENSE.clear()
     gemm._VALIDATED_MASKED.clear()
     gemm._VALIDATED_PACKED.clear()
+    from . import bf16
+    bf16._VALIDATED_BF16.clear()
 
 
 def last_forced_config() -> str:

@@ -354,3 +354,117 @@ def generate_k_grouped_contiguous(num_groups: int, m: int, n: int, ks: List[int]
         a_op, b_op = (a_q, sfa), (b_q, sfb)
     layout = torch.tensor(ks, device=device, dtype=torch.int32)
     return KGroupedCase(a_op, b_op, a_groups, b_groups, c, c.clone(), ref_d, list(ks), layout)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# BF16 GEMMs (the reference's tests/generators.py:115-187 with dtype = torch.bfloat16, :301-408): the operands are the BF16 tensors
+# themselves, the reference result the FP32 product cast to the output dtype (``ref_d``; ``c`` added in FP32 when accumulating).
+# ---------------------------------------------------------------------------------------------------------------------
+BF16_FP32_OUTPUT_NK = [(256, 7168), (129280, 7168)]
+
+
+def enumerate_bf16_normal() -> Iterator[Tuple[int, int, int, bool, bool, bool, torch.dtype]]:
+    """(m, n, k, a_k_major, b_k_major, accumulate, out_dtype): forward m in {1, 128, 4096} over the BF16-output and FP32-output (n, k)
+    lists, accumulating with c is d, then the backward dgrad / wgrad forms (MN-major operands)."""
+    nk = [(n, k, torch.bfloat16) for n, k in DENSE_NK] + [(n, k, torch.float) for n, k in BF16_FP32_OUTPUT_NK]
+    for m in DENSE_M_FWD:
+        for n, k, out in nk:
+            for acc in (False, True):
+                yield m, n, k, True, True, acc, out
+    for n, k in DENSE_NK:
+        yield 4096, k, n, True, False, False, torch.bfloat16              # dgrad (nn)
+        yield n, 4096, k, False, False, True, torch.float                 # wgrad (tn), FP32 accumulate
+        yield n, 4096, k, False, False, False, torch.bfloat16             # wgrad, BF16
+
+
+def enumerate_bf16_m_grouped_contiguous() -> Iterator[Tuple[int, int, int, int, bool, bool]]:
+    for use_psum in (False, True):
+        for groups, expected in CONTIGUOUS_GROUPS:
+            for n, k in GROUPED_NK:
+                for b_k_major in (True, False):
+                    yield groups, expected, n, k, b_k_major, use_psum
+
+
+def enumerate_bf16_m_grouped_masked() -> Iterator[Tuple[int, int, int, int, int]]:
+    for groups, expected in MASKED_GROUPS:
+        for n, k in GROUPED_NK:
+            yield groups, MASKED_MAX_M, expected, n, k
+
+
+@dataclass
+class Bf16DenseCase:
+    a: torch.Tensor             # [m, k] (a_k_major) or an MN-major [k, m] tensor for the tn / tt forms
+    b: torch.Tensor             # [n, k] or [k, n]
+    d: torch.Tensor
+    c: Optional[torch.Tensor]
+    ref_d: torch.Tensor
+
+
+def generate_bf16_normal(m: int, n: int, k: int, a_k_major: bool = True, b_k_major: bool = True, accumulate: bool = False,
+                         out_dtype: torch.dtype = torch.bfloat16, device: str = 'cuda') -> Bf16DenseCase:
+    a = torch.randn((m, k), device=device, dtype=torch.bfloat16)
+    b = torch.randn((n, k), device=device, dtype=torch.bfloat16)
+    d = torch.randn((m, n), device=device, dtype=out_dtype) * 32 if accumulate else torch.empty((m, n), device=device, dtype=out_dtype)
+    c = d if accumulate else None
+    ref_d = (a.float() @ b.float().t() + (c.float() if accumulate else 0)).to(out_dtype)
+    a = a if a_k_major else a.t().contiguous()
+    b = b if b_k_major else b.t().contiguous()
+    return Bf16DenseCase(a, b, d, c, ref_d)
+
+
+@dataclass
+class Bf16ContiguousCase:
+    m: int
+    a: torch.Tensor             # [m, k]
+    b: torch.Tensor             # [g, n, k] or (b_k_major False) [g, k, n]
+    d: torch.Tensor
+    layout: torch.Tensor        # per-row group ids (-1 = padding) or, psum, the groups' cumulative ends
+    ref_d: torch.Tensor
+    group_rows: List[Tuple[int, int, int]]      # (group, first row, end row)
+
+
+def generate_bf16_m_grouped_contiguous(num_groups: int, expected_m_per_group: int, n: int, k: int, b_k_major: bool = True,
+                                       use_psum_layout: bool = False, device: str = 'cuda') -> Bf16ContiguousCase:
+    align_m = runtime.get_mk_alignment_for_contiguous_layout()
+    sizes = [int(expected_m_per_group * random.uniform(0.7, 1.3)) for _ in range(num_groups)]
+    starts, rows = [], 0
+    for s in sizes:
+        starts.append(rows)
+        rows += align(s, align_m)
+    m = rows
+    a = torch.randn((m, k), device=device, dtype=torch.bfloat16)
+    b = torch.randn((num_groups, n, k), device=device, dtype=torch.bfloat16)
+    d = torch.empty((m, n), device=device, dtype=torch.bfloat16)
+    ref_d = torch.zeros((m, n), device=device, dtype=torch.bfloat16)
+    layout = torch.full((m,), -1, device=device, dtype=torch.int32)
+    group_rows = []
+    for g, (s, start) in enumerate(zip(sizes, starts)):
+        layout[start:start + s] = g
+        a[start + s:start + align(s, align_m)] = 0          # (the reference's padding rows: zeros, tests/generators.py:327-366)
+        ref_d[start:start + s] = (a[start:start + s].float() @ b[g].float().t()).bfloat16()
+        group_rows.append((g, start, start + s))
+    if use_psum_layout:
+        layout = torch.tensor([start + s for s, start in zip(sizes, starts)], device=device, dtype=torch.int32)
+    b = b if b_k_major else b.transpose(1, 2).contiguous()
+    return Bf16ContiguousCase(m, a, b, d, layout, ref_d, group_rows)
+
+
+@dataclass
+class Bf16MaskedCase:
+    a: torch.Tensor             # [g, max_m, k]
+    b: torch.Tensor             # [g, n, k]
+    d: torch.Tensor             # [g, max_m, n]
+    masked_m: torch.Tensor
+    ref_d: torch.Tensor
+
+
+def generate_bf16_m_grouped_masked(num_groups: int, max_m: int, expected_m_per_group: int, n: int, k: int,
+                                   masked_ms: Optional[List[int]] = None, device: str = 'cuda') -> Bf16MaskedCase:
+    a = torch.randn((num_groups, max_m, k), device=device, dtype=torch.bfloat16)
+    b = torch.randn((num_groups, n, k), device=device, dtype=torch.bfloat16)
+    d = torch.empty((num_groups, max_m, n), device=device, dtype=torch.bfloat16)
+    ref_d = torch.einsum('gmk,gnk->gmn', a.float(), b.float()).bfloat16()
+    if masked_ms is None:
+        masked_ms = [min(max_m, int(expected_m_per_group * random.uniform(0.7, 1.3))) for _ in range(num_groups)]
+    masked_m = torch.tensor(masked_ms, device=device, dtype=torch.int32)
+    return Bf16MaskedCase(a, b, d, masked_m, ref_d)

@@ -510,6 +510,36 @@ int dg_operand_plan(int gemm_type, const void* a, const void* b, int m, int n, i
 const char* dg_last_error(void);
 const char* dg_version(void);
 
+/* BF16 GEMMs (reference csrc/apis/gemm.hpp:404-560: bf16_gemm_nt and the M-grouped contiguous / masked forms).
+ *   a, b : BF16, K-major (unit stride along K), 16-byte aligned base, row strides in ELEMENTS, multiples of 8 (16 bytes); k % 8 == 0
+ *          (k need not be a multiple of the 64-value K block: the kernels zero-fill the tail).  MN-major operands are re-majored by the
+ *          caller (dg_transpose_bf16).
+ *   d    : row-major, row stride d_stride_m (elements).  Arithmetic: D = round_to_d_dtype(acc + float(D) if accumulate else acc), acc the
+ *          FP32 sum of the exact BF16 products, rounded ONCE (an accumulating BF16 output is not rounded twice).
+ * dg_bf16_gemm_nt: d_dtype DG_BF16 or DG_FP32.  workspace (optional, 16-byte aligned, workspace_bytes long; dg_split_k_workspace_bytes() is
+ *   enough): dense problems at m <= 64 whose tiles fill at most half of the CUs are cut along K, FP32 partials in the workspace and a
+ *   summing launch on the same stream; NULL = never cut.  k == 0 is the caller's (D = C or 0). */
+int dg_bf16_gemm_nt(const void* a, const void* b, void* d, int m, int n, int k, int64_t a_stride_m, int64_t b_stride_n,
+                    int64_t d_stride_m, int d_dtype, int accumulate, void* workspace, int64_t workspace_bytes, void* stream);
+/* M-grouped contiguous: a [m, k], b [num_groups, n, k] (group stride b_stride_g elements), d [m, n] BF16; grouped_layout as for
+ * dg_m_grouped_fp8_gemm_nt_contiguous (per-row group ids, -1 rows written as zeros; or, use_psum != 0, the groups' cumulative ends, each
+ * group starting at the previous end rounded up to m_alignment).  m_alignment must be a multiple of 64. */
+int dg_m_grouped_bf16_gemm_nt_contiguous(const void* a, const void* b, void* d, const int32_t* grouped_layout, int num_groups,
+                                         int m, int n, int k, int64_t a_stride_m, int64_t b_stride_g, int64_t b_stride_n,
+                                         int64_t d_stride_m, int use_psum, int m_alignment, void* stream);
+/* M-grouped masked: a [num_groups, m_max, k], b [num_groups, n, k], d [num_groups, m_max, n] BF16; rows at and past masked_m[g] (device)
+ * are not written.  expected_m: selection hint. */
+int dg_m_grouped_bf16_gemm_nt_masked(const void* a, const void* b, void* d, const int32_t* masked_m, int num_groups, int m_max, int n,
+                                     int k, int expected_m, int64_t a_stride_g, int64_t a_stride_m, int64_t b_stride_g, int64_t b_stride_n,
+                                     int64_t d_stride_g, int64_t d_stride_m, void* stream);
+/* dst[b][c][r] = src[b][r][c] for BF16 elements (leading dimensions and batch strides in elements): the re-majoring pass of MN-major BF16
+ * operands in front of the K-major kernels. */
+int dg_transpose_bf16(const void* src, void* dst, int batches, int rows, int cols,
+                      int64_t src_ld, int64_t dst_ld, int64_t src_batch_stride, int64_t dst_batch_stride, void* stream);
+/* Name of the BF16 configuration the automatic selection would launch (gemm_type as dg_select_config: 0 dense, 1 contiguous, 2 contiguous
+ * psum, 3 masked), "" if none; nothing is launched.  Respects dg_set_num_cus, ignores a forced configuration. */
+const char* dg_bf16_select_config(int gemm_type, int m, int n, int k, int num_groups, int expected_m, int m_alignment, int has_workspace);
+
 #ifdef __cplusplus
 }
 #endif
