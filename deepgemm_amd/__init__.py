@@ -18,6 +18,9 @@ from .bf16 import (                                   # noqa: F401
     bf16_gemm_nt, bf16_gemm_nn, bf16_gemm_tn, bf16_gemm_tt,
     m_grouped_bf16_gemm_nt_contiguous, m_grouped_bf16_gemm_nn_contiguous, m_grouped_bf16_gemm_nt_masked, bf16_m_grouped_gemm_nt_masked,
 )
+from .attention import (                              # noqa: F401
+    fp8_fp4_mqa_logits, fp8_mqa_logits, get_paged_mqa_logits_metadata, fp8_fp4_paged_mqa_logits, fp8_paged_mqa_logits,
+)
 from .layout import transform_sf_into_required_layout                 # noqa: F401
 from .quant import (fused_per_token_cast_to_fp8, fused_per_block_cast_to_fp8,      # noqa: F401
                     fused_per_channel_cast_to_fp8)

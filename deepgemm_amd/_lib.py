@@ -54,6 +54,10 @@ SIGNATURES = {
     'dg_m_grouped_bf16_gemm_nt_masked': (_i32, [_vp] * 4 + [_i32] * 5 + [_i64] * 6 + [_vp]),
     'dg_transpose_bf16': (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _vp]),
     'dg_bf16_select_config': (_cp, [_i32] * 8),
+    'dg_fp8_mqa_logits': (_i32, [_vp] * 7 + [_i32] * 4 + [_i64] * 2 + [_i32] * 3 + [_vp]),
+    'dg_clean_logits': (_i32, [_vp] * 3 + [_i32] * 2 + [_i64, _i32, _vp]),
+    'dg_paged_mqa_logits_metadata': (_i32, [_vp] * 2 + [_i32] * 4 + [_vp]),
+    'dg_fp8_paged_mqa_logits': (_i32, [_vp] * 7 + [_i32] * 6 + [_i64] * 4 + [_i32] * 4 + [_vp]),
     'dg_set_num_cus': (_i32, [_i32]),
     'dg_get_num_cus': (_i32, []),
     'dg_set_forced_config': (_i32, [_cp]),

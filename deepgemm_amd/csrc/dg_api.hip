@@ -16,6 +16,7 @@
 #include "fp8_gemm_quad.hpp"
 #include "fp8_gemm_moe.hpp"
 #include "bf16_gemm_kernels.hpp"
+#include "mqa_logits_kernels.hpp"
 #ifndef DG_MONOLITHIC   // (the default build: the template kernels are compiled by the dg_shard.hip units, see kernel_instances.inc)
 namespace dg {
 #define DG_HAVE_MOE_HPP 1
@@ -1572,6 +1573,136 @@ bool bf16_operand_ok(const void* ptr, int64_t row_stride, int64_t group_stride =
 }
 
 }  // namespace
+
+// ---- indexer MQA logits (mqa_logits_kernels.hpp) ----
+
+namespace {
+
+int mqa_head_index(int h) { return h == 8 ? 0 : h == 16 ? 1 : h == 32 ? 2 : h == 64 ? 3 : -1; }
+int mqa_dim_index(int d) { return d == 32 ? 0 : d == 64 ? 1 : d == 128 ? 2 : -1; }
+
+using MqaKernelFn = void (*)(const dg::mqa::MqaParams);
+
+#define DG_MQA_DENSE_ROW(H) {dg::mqa::dg_mqa_logits_kernel<H, 32>, dg::mqa::dg_mqa_logits_kernel<H, 64>, dg::mqa::dg_mqa_logits_kernel<H, 128>}
+const MqaKernelFn kMqaDense[4][3] = {DG_MQA_DENSE_ROW(8), DG_MQA_DENSE_ROW(16), DG_MQA_DENSE_ROW(32), DG_MQA_DENSE_ROW(64)};
+#undef DG_MQA_DENSE_ROW
+
+// paged kernels by [head index][dim index][log2 MT]; a group holds at least one token (MT * 16 >= H): none below MT = 2 at H = 32, 4 at 64
+template <int H, int D, int MT>
+constexpr MqaKernelFn mqa_paged_or_null() {
+    if constexpr (MT * 16 >= H)
+        return dg::mqa::dg_paged_mqa_logits_kernel<H, D, MT>;
+    else
+        return nullptr;
+}
+#define DG_MQA_PAGED_D(H, D) {mqa_paged_or_null<H, D, 1>(), mqa_paged_or_null<H, D, 2>(), mqa_paged_or_null<H, D, 4>(), mqa_paged_or_null<H, D, 8>()}
+#define DG_MQA_PAGED_H(H) {DG_MQA_PAGED_D(H, 32), DG_MQA_PAGED_D(H, 64), DG_MQA_PAGED_D(H, 128)}
+const MqaKernelFn kMqaPaged[4][3][4] = {DG_MQA_PAGED_H(8), DG_MQA_PAGED_H(16), DG_MQA_PAGED_H(32), DG_MQA_PAGED_H(64)};
+#undef DG_MQA_PAGED_H
+#undef DG_MQA_PAGED_D
+
+bool mqa_dtypes_ok(int logits_dtype, int weights_dtype) {
+    return (logits_dtype == DG_FP32 || logits_dtype == DG_BF16) && (weights_dtype == DG_FP32 || weights_dtype == DG_BF16) &&
+           (weights_dtype == DG_FP32 || logits_dtype == DG_BF16);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dg_fp8_mqa_logits(const void* q, const void* kv, const float* kv_sf, const void* weights, const int32_t* ks, const int32_t* ke,
+                      void* logits, int seq_len, int seq_len_kv, int num_heads, int head_dim, int64_t weights_stride, int64_t logits_stride,
+                      int max_seqlen_k, int logits_dtype, int weights_dtype, void* stream) {
+    const int hi = mqa_head_index(num_heads), di = mqa_dim_index(head_dim);
+    DG_CHECK(hi >= 0 && di >= 0);
+    DG_CHECK(seq_len >= 0 && seq_len_kv >= 0 && max_seqlen_k >= 0);
+    DG_CHECK(mqa_dtypes_ok(logits_dtype, weights_dtype));
+    if (seq_len == 0 || seq_len_kv == 0)
+        return 0;
+    DG_CHECK(q != nullptr && kv != nullptr && kv_sf != nullptr && weights != nullptr && ks != nullptr && ke != nullptr && logits != nullptr);
+    DG_CHECK(weights_stride >= num_heads && logits_stride >= (max_seqlen_k > 0 ? max_seqlen_k : seq_len_kv));
+    dg::mqa::MqaParams p{};
+    p.q = static_cast<const uint8_t*>(q); p.kv = static_cast<const uint8_t*>(kv); p.kv_sf = kv_sf;
+    p.weights = weights; p.ks = ks; p.ke = ke; p.logits = logits;
+    p.logits_stride = logits_stride; p.w_stride = weights_stride;
+    p.seq_len = seq_len; p.seq_len_kv = seq_len_kv; p.max_seqlen_k = max_seqlen_k;
+    p.logits_bf16 = logits_dtype == DG_BF16; p.weights_bf16 = weights_dtype == DG_BF16;
+    // KV chunks of 256-column multiples, enough of them for ~2048 workgroups; the chunking never changes a value (each element is
+    // computed by one lane with one fixed reduction)
+    const int tokens_per_wg = 128 / num_heads * dg::mqa::kDenseWaves;
+    const int q_groups = (seq_len + tokens_per_wg - 1) / tokens_per_wg;
+    const int max_chunks = (seq_len_kv + 255) / 256;
+    const int chunks = std::max(1, std::min(max_chunks, (2048 + q_groups - 1) / q_groups));
+    p.kv_chunk = ((seq_len_kv + chunks - 1) / chunks + 255) / 256 * 256;
+    const dim3 grid(q_groups, (seq_len_kv + p.kv_chunk - 1) / p.kv_chunk);
+    DG_CHECK(grid.y <= 65535);
+    hipLaunchKernelGGL(kMqaDense[hi][di], grid, dim3(dg::mqa::kDenseWaves * 64), 0, static_cast<hipStream_t>(stream), p);
+    DG_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int dg_clean_logits(const int32_t* ks, const int32_t* ke, void* logits, int seq_len, int seq_len_kv, int64_t logits_stride,
+                    int logits_dtype, void* stream) {
+    DG_CHECK(seq_len >= 0 && seq_len_kv >= 0);
+    DG_CHECK(logits_dtype == DG_FP32 || logits_dtype == DG_BF16);
+    if (seq_len == 0 || seq_len_kv == 0)
+        return 0;
+    DG_CHECK(ks != nullptr && ke != nullptr && logits != nullptr && logits_stride >= seq_len_kv);
+    dg::mqa::MqaParams p{};
+    p.ks = ks; p.ke = ke; p.logits = logits; p.logits_stride = logits_stride;
+    p.seq_len = seq_len; p.seq_len_kv = seq_len_kv; p.logits_bf16 = logits_dtype == DG_BF16;
+    // rows on x, column chunks on y (strided inside the kernel past 65535 chunks): no size limit beyond the int arguments
+    const dim3 grid(seq_len, std::min((seq_len_kv + dg::mqa::kCleanCols - 1) / dg::mqa::kCleanCols, 65535));
+    hipLaunchKernelGGL(dg::mqa::dg_mqa_clean_logits_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    DG_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int dg_paged_mqa_logits_metadata(const int32_t* context_lens, int32_t* schedule, int batch, int next_n, int block_kv, int num_sms,
+                                 void* stream) {
+    DG_CHECK(block_kv == 32 || block_kv == 64);
+    DG_CHECK(batch >= 0 && next_n >= 1 && num_sms >= 1);
+    DG_CHECK(schedule != nullptr && (batch == 0 || context_lens != nullptr));
+    hipLaunchKernelGGL(dg::mqa::dg_paged_mqa_logits_metadata_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream),
+                       context_lens, schedule, batch, next_n, num_sms);
+    DG_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int dg_fp8_paged_mqa_logits(const void* q, const void* kv_cache, const void* weights, const int32_t* context_lens, const int32_t* block_table,
+                            const int32_t* schedule, void* logits, int batch, int next_n, int num_heads, int head_dim, int block_kv,
+                            int max_blocks, int64_t kv_block_stride, int64_t block_table_stride, int64_t weights_stride,
+                            int64_t logits_stride, int max_context_len, int num_sms, int logits_dtype, int weights_dtype, void* stream) {
+    const int hi = mqa_head_index(num_heads), di = mqa_dim_index(head_dim);
+    DG_CHECK(hi >= 0 && di >= 0);
+    DG_CHECK(block_kv == 32 || block_kv == 64);
+    DG_CHECK(batch >= 0 && next_n >= 1 && max_blocks >= 0 && max_context_len >= 0 && num_sms >= 1);
+    DG_CHECK(mqa_dtypes_ok(logits_dtype, weights_dtype));
+    DG_CHECK(kv_block_stride % 4 == 0 && kv_block_stride >= static_cast<int64_t>(block_kv) * (head_dim + 4));
+    if (batch == 0 || max_context_len == 0 || max_blocks == 0)
+        return 0;
+    DG_CHECK(q != nullptr && kv_cache != nullptr && weights != nullptr && context_lens != nullptr && block_table != nullptr &&
+             schedule != nullptr && logits != nullptr);
+    DG_CHECK(weights_stride >= num_heads && logits_stride >= max_context_len && block_table_stride >= max_blocks);
+    // the wave's Q group: all next_n tokens when they fit 128 rows, else groups of 128 / H tokens; MT = its 16-row tiles (>= H / 16)
+    const int tokens = std::min(next_n, 128 / num_heads);
+    const int tiles = (tokens * num_heads + 15) / 16;
+    const int mt_index = tiles <= 1 ? 0 : tiles <= 2 ? 1 : tiles <= 4 ? 2 : 3;
+    const MqaKernelFn fn = kMqaPaged[hi][di][mt_index];
+    DG_CHECK(fn != nullptr);
+    dg::mqa::MqaParams p{};
+    p.q = static_cast<const uint8_t*>(q); p.kv = static_cast<const uint8_t*>(kv_cache); p.weights = weights;
+    p.context_lens = context_lens; p.block_table = block_table; p.schedule = schedule; p.logits = logits;
+    p.logits_stride = logits_stride; p.w_stride = weights_stride; p.kv_block_stride = kv_block_stride;
+    p.block_table_stride = block_table_stride;
+    p.batch = batch; p.next_n = next_n; p.block_kv = block_kv; p.max_blocks = max_blocks; p.max_context_len = max_context_len;
+    p.logits_bf16 = logits_dtype == DG_BF16; p.weights_bf16 = weights_dtype == DG_BF16;
+    hipLaunchKernelGGL(fn, dim3(num_sms), dim3(dg::mqa::kPagedWaves * 64), 0, static_cast<hipStream_t>(stream), p);
+    DG_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"
 
 extern "C" {
 

@@ -540,6 +540,35 @@ int dg_transpose_bf16(const void* src, void* dst, int batches, int rows, int col
  * psum, 3 masked), "" if none; nothing is launched.  Respects dg_set_num_cus, ignores a forced configuration. */
 const char* dg_bf16_select_config(int gemm_type, int m, int n, int k, int num_groups, int expected_m, int m_alignment, int has_workspace);
 
+/* Indexer MQA logits, FP8 operands (reference csrc/apis/attention.hpp: fp8_fp4_mqa_logits, get_paged_mqa_logits_metadata,
+ * fp8_fp4_paged_mqa_logits).  num_heads in {8, 16, 32, 64}, head_dim in {32, 64, 128}; logits_dtype / weights_dtype DG_FP32 or DG_BF16
+ * (BF16 weights only with BF16 logits).  Every element is
+ *   logits[i, j] = sum_h w[i, h] * relu(sf[j] * sum_d q[i, h, d] * kv[j, d])
+ * with exact FP8 products, FP32 accumulation in one fixed order whatever the work split, and one rounding to BF16 (nearest even).
+ * dg_fp8_mqa_logits (dense): q [S, H, D] and kv [S_kv, D] contiguous e4m3, kv_sf [S_kv] FP32, weights [S, H] (row stride
+ *   weights_stride elements), ks / ke [S] int32 on the device; logits row stride logits_stride elements.  Row i gets the columns
+ *   max(ks[i], 0) <= j < min(ke[i], S_kv) -- at column j, or (max_seqlen_k > 0, compressed) at column j - ks[i] when that is below
+ *   max_seqlen_k; nothing else is written. */
+int dg_fp8_mqa_logits(const void* q, const void* kv, const float* kv_sf, const void* weights, const int32_t* ks, const int32_t* ke,
+                      void* logits, int seq_len, int seq_len_kv, int num_heads, int head_dim, int64_t weights_stride, int64_t logits_stride,
+                      int max_seqlen_k, int logits_dtype, int weights_dtype, void* stream);
+/* -inf in every column j < seq_len_kv of rows i < seq_len outside max(ks[i], 0) <= j < min(ke[i], seq_len_kv). */
+int dg_clean_logits(const int32_t* ks, const int32_t* ke, void* logits, int seq_len, int seq_len_kv, int64_t logits_stride,
+                    int logits_dtype, void* stream);
+/* The paged kernel's work split over num_sms workgroups, computed on the device from context_lens [batch, next_n] (int32): schedule
+ * [num_sms + 1, 2] int32.  No host synchronisation.  block_kv must be 32 or 64. */
+int dg_paged_mqa_logits_metadata(const int32_t* context_lens, int32_t* schedule, int batch, int next_n, int block_kv, int num_sms,
+                                 void* stream);
+/* dg_fp8_paged_mqa_logits (decode): q [batch, next_n, H, D] contiguous e4m3; kv_cache: block b at byte kv_cache + b * kv_block_stride,
+ *   block_kv FP8 rows of D bytes then block_kv FP32 scales (kv_block_stride % 4 == 0); weights [batch * next_n, H]; context_lens
+ *   [batch, next_n]; block_table [batch, max_blocks] (row stride block_table_stride); schedule from dg_paged_mqa_logits_metadata with
+ *   num_sms + 1 rows.  Row b * next_n + t gets the columns j < min(context_lens[b, t], max_context_len); column j reads row j % block_kv
+ *   of block block_table[b, j / block_kv].  Block-table entries at or past ceil(max_t context_lens[b, t] / block_kv) are never read. */
+int dg_fp8_paged_mqa_logits(const void* q, const void* kv_cache, const void* weights, const int32_t* context_lens, const int32_t* block_table,
+                            const int32_t* schedule, void* logits, int batch, int next_n, int num_heads, int head_dim, int block_kv,
+                            int max_blocks, int64_t kv_block_stride, int64_t block_table_stride, int64_t weights_stride,
+                            int64_t logits_stride, int max_context_len, int num_sms, int logits_dtype, int weights_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,7 +157,7 @@ def report():
             kernels[cur].append(line.split('//')[0].strip())
     out = []
     for name, body in kernels.items():
-        if name not in meta or 'gemm' not in name:
+        if name not in meta or ('gemm' not in name and 'mqa_logits' not in name):
             continue
         mfma = [i for i, ins in enumerate(body) if ins.startswith('v_mfma')]
         # the K loop: from the first MFMA to the first backward branch behind it (kernels with a K-tail stage have more MFMAs after
@@ -171,7 +171,7 @@ def report():
                     break
         loop = body[mfma[0]:end + 1] if mfma else []
         # readable name without a demangler: _ZN2dg22dg_fp8_gemm_duo_kernelILi256ELi256ELi2ELi4ELi0EEEvNS_10GemmParamsE
-        m = re.match(r'_ZN2dg\d+(\w+?)(?:I(.*?)EEv|Ev)', name)
+        m = re.match(r'_ZN2dg(?:3mqa)?\d+(\w+?)(?:I(.*?)EEv|Ev)', name)
         pretty = name if not m else m.group(1) + ('<' + ','.join(re.findall(r'L[ib](\d+)E', m.group(2))) + '>' if m.group(2) else '')
         out.append({'kernel': pretty, 'symbol': name, **meta[name],
                     'mfma_range_instructions': len(loop),
