@@ -21,6 +21,7 @@ from .bf16 import (                                   # noqa: F401
 from .attention import (                              # noqa: F401
     fp8_fp4_mqa_logits, fp8_mqa_logits, get_paged_mqa_logits_metadata, fp8_fp4_paged_mqa_logits, fp8_paged_mqa_logits,
 )
+from .hyperconnection import tf32_hc_prenorm_gemm                       # noqa: F401
 from .layout import transform_sf_into_required_layout                 # noqa: F401
 from .quant import (fused_per_token_cast_to_fp8, fused_per_block_cast_to_fp8,      # noqa: F401
                     fused_per_channel_cast_to_fp8)

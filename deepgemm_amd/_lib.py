@@ -58,6 +58,8 @@ SIGNATURES = {
     'dg_clean_logits': (_i32, [_vp] * 3 + [_i32] * 2 + [_i64, _i32, _vp]),
     'dg_paged_mqa_logits_metadata': (_i32, [_vp] * 2 + [_i32] * 4 + [_vp]),
     'dg_fp8_paged_mqa_logits': (_i32, [_vp] * 7 + [_i32] * 6 + [_i64] * 4 + [_i32] * 4 + [_vp]),
+    'dg_tf32_hc_prenorm_gemm': (_i32, [_vp] * 4 + [_i32] * 3 + [_i64] * 4 + [_i32, _vp, _i64, _vp]),
+    'dg_hc_prenorm_pieces': (_i32, [_i32] * 4 + [_i64]),
     'dg_set_num_cus': (_i32, [_i32]),
     'dg_get_num_cus': (_i32, []),
     'dg_set_forced_config': (_i32, [_cp]),

@@ -18,7 +18,7 @@ import tempfile
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB_PATH = os.path.join(CSRC, 'libdeepgemm_amd.so')
 SOURCES = ['dg_api.hip', 'dg_shard.hip', 'kernel_instances.inc']
-NUM_SHARDS = 12                         # shard ids 0 .. NUM_SHARDS - 1 of kernel_instances.inc
+NUM_SHARDS = 13                         # shard ids 0 .. NUM_SHARDS - 1 of kernel_instances.inc
 MONOLITHIC = os.environ.get('DG_MONOLITHIC', '') not in ('', '0')
 # Per-shard compiler flags.  Shard 9 (the K-grouped quad kernels that read MN-major operands in place): their block body holds ~130 inline-asm
 # statements more than the K-major form's, which takes the fully unrolled K-block loops over LLVM's `#pragma unroll` cost limit (16 K units); past
@@ -26,7 +26,7 @@ MONOLITHIC = os.environ.get('DG_MONOLITHIC', '') not in ('', '0')
 # scratch operations in the loop) -- the mechanism behind every "one more copy of the block body and the accumulators go to memory" note in the
 # sources.  The other shards are compiled as they always were.
 SHARD_FLAGS = {9: ['-mllvm', '-pragma-unroll-threshold=200000']}
-HEADERS = ['fp8_gemm_kernels.hpp', 'fp8_gemm_quad.hpp', 'fp8_gemm_moe.hpp', 'bf16_gemm_kernels.hpp', 'mqa_logits_kernels.hpp', os.path.join('..', '..', 'include', 'deepgemm_amd.h')]
+HEADERS = ['fp8_gemm_kernels.hpp', 'fp8_gemm_quad.hpp', 'fp8_gemm_moe.hpp', 'bf16_gemm_kernels.hpp', 'mqa_logits_kernels.hpp', 'hc_prenorm_kernels.hpp', os.path.join('..', '..', 'include', 'deepgemm_amd.h')]
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-slp-vectorize'] + \
         (['-DDG_MONOLITHIC', '-mllvm', '-pragma-unroll-threshold=200000'] if MONOLITHIC else [])      # (one unit: shard 9's flag for all, see SHARD_FLAGS)

@@ -17,6 +17,7 @@
 #include "fp8_gemm_moe.hpp"
 #include "bf16_gemm_kernels.hpp"
 #include "mqa_logits_kernels.hpp"
+#include "hc_prenorm_kernels.hpp"
 #ifndef DG_MONOLITHIC   // (the default build: the template kernels are compiled by the dg_shard.hip units, see kernel_instances.inc)
 namespace dg {
 #define DG_HAVE_MOE_HPP 1
@@ -1699,6 +1700,86 @@ int dg_fp8_paged_mqa_logits(const void* q, const void* kv_cache, const void* wei
     p.logits_bf16 = logits_dtype == DG_BF16; p.weights_bf16 = weights_dtype == DG_BF16;
     hipLaunchKernelGGL(fn, dim3(num_sms), dim3(dg::mqa::kPagedWaves * 64), 0, static_cast<hipStream_t>(stream), p);
     DG_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- hyper-connection pre-norm GEMM (hc_prenorm_kernels.hpp) ----
+
+namespace {
+
+using HcKernelFn = void (*)(const dg::hc::HcParams);
+const HcKernelFn kHcKernels[2][2] = {{dg::hc::dg_hc_prenorm_gemm_kernel<1, 1>, dg::hc::dg_hc_prenorm_gemm_kernel<1, 2>},
+                                     {dg::hc::dg_hc_prenorm_gemm_kernel<8, 1>, dg::hc::dg_hc_prenorm_gemm_kernel<8, 2>}};
+
+// Row tile of a launch: 16 rows while m <= 64 (the MFMAs of a taller tile would multiply zeros), else 128.
+int hc_tile_rows(int m) { return m <= 64 ? 16 : 128; }
+
+// K pieces of a num_splits=None launch: enough work items for two workgroups per CU, at least one K block per wave and piece, at most
+// 4 load batches of the sum launch (whose per-element chain is the latency of the small shapes), and the partials ([pieces][m][n + 1]
+// FP32) inside the workspace; 1 = no cut, the kernel writes d and sqr_sum itself.
+int hc_pieces(int m, int n, int k, int64_t workspace_bytes) {
+    const int tiles = (m + hc_tile_rows(m) - 1) / hc_tile_rows(m);
+    const int64_t per_piece = static_cast<int64_t>(m) * (n + 1) * static_cast<int64_t>(sizeof(float));
+    int pieces = (2 * num_cus() + tiles - 1) / tiles;
+    pieces = std::min({pieces, std::max(1, k / dg::hc::kBlockK / dg::hc::kWaves), 4 * dg::hc::kSumBatch});
+    pieces = static_cast<int>(std::min<int64_t>(pieces, workspace_bytes / per_piece));
+    return std::max(1, pieces);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dg_hc_prenorm_pieces(int m, int n, int k, int num_splits, int64_t workspace_bytes) {
+    if (m <= 0 || n <= 0 || k <= 0)
+        return 0;
+    return num_splits > 0 ? num_splits : hc_pieces(m, n, k, workspace_bytes);
+}
+
+int dg_tf32_hc_prenorm_gemm(const void* a, const float* b, float* d, float* sqr_sum, int m, int n, int k, int64_t a_stride,
+                            int64_t b_stride, int64_t d_stride_m, int64_t d_stride_split, int num_splits, void* workspace,
+                            int64_t workspace_bytes, void* stream) {
+    DG_CHECK(m >= 0 && n > 0 && k > 0 && num_splits >= 0);                              // reference hyperconnection.hpp
+    DG_CHECK(n % 8 == 0 && n <= 32 && k % dg::hc::kBlockK == 0);                         // reference sm90_tf32_hc_prenorm_gemm.hpp
+    DG_CHECK(a_stride >= k && b_stride >= k && d_stride_m >= n && (num_splits == 0 || d_stride_split >= 0));
+    if (m == 0)
+        return 0;
+    DG_CHECK(a != nullptr && b != nullptr && d != nullptr && sqr_sum != nullptr);
+    const int rows = hc_tile_rows(m);
+    // every in-range buffer offset of a workgroup fits 31 bits (its bases sit at the row tile and the K piece)
+    DG_CHECK((static_cast<int64_t>(rows) - 1) * a_stride * 2 + static_cast<int64_t>(k) * 2 < (int64_t{1} << 31));
+    DG_CHECK(static_cast<int64_t>(n - 1) * b_stride * 4 + static_cast<int64_t>(k) * 4 < (int64_t{1} << 31));
+    const int pieces = num_splits > 0 ? num_splits : hc_pieces(m, n, k, workspace != nullptr ? workspace_bytes : 0);
+    const bool cut = num_splits == 0 && pieces > 1;
+    dg::hc::HcParams p{};
+    p.a = static_cast<const uint8_t*>(a);
+    p.b = b;
+    p.m = m; p.n = n; p.k = k;
+    p.a_stride = a_stride; p.b_stride = b_stride;
+    p.tiles = (m + rows - 1) / rows;
+    p.splits = pieces;
+    if (cut) {                          // partials [pieces][m][n] then [pieces][m], summed in piece order by the second launch
+        float* ws = static_cast<float*>(workspace);
+        p.d = ws; p.d_sm = n; p.d_ss = static_cast<int64_t>(m) * n;
+        p.s = ws + static_cast<int64_t>(pieces) * m * n; p.s_ss = m;
+    } else {
+        p.d = d; p.d_sm = d_stride_m; p.d_ss = num_splits > 0 ? d_stride_split : 0;
+        p.s = sqr_sum; p.s_ss = m;
+    }
+    p.d_vec = reinterpret_cast<uintptr_t>(p.d) % 16 == 0 && p.d_sm % 4 == 0 && p.d_ss % 4 == 0;
+    DG_CHECK(static_cast<int64_t>(p.tiles) * pieces <= 0x7fffffff);
+    const HcKernelFn fn = kHcKernels[rows == 128][n > 16];
+    hipLaunchKernelGGL(fn, dim3(p.tiles * pieces), dim3(dg::hc::kWaves * 64), 0, static_cast<hipStream_t>(stream), p);
+    DG_HIP_CHECK(hipGetLastError());
+    if (cut) {
+        const int64_t items = static_cast<int64_t>(m) * (n + 1);
+        const int grid = static_cast<int>(std::min<int64_t>((items + 255) / 256, 4 * static_cast<int64_t>(num_cus())));
+        hipLaunchKernelGGL(dg::hc::dg_hc_prenorm_sum_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream),
+                           static_cast<const float*>(workspace), pieces, m, n, d, d_stride_m, sqr_sum);
+        DG_HIP_CHECK(hipGetLastError());
+    }
     return 0;
 }
 

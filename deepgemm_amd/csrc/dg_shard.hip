@@ -11,6 +11,7 @@
 #include "fp8_gemm_moe.hpp"
 #include "bf16_gemm_kernels.hpp"
 #include "mqa_logits_kernels.hpp"
+#include "hc_prenorm_kernels.hpp"
 #define DG_HAVE_MOE_HPP 1
 
 namespace dg {

@@ -569,6 +569,22 @@ int dg_fp8_paged_mqa_logits(const void* q, const void* kv_cache, const void* wei
                             int max_blocks, int64_t kv_block_stride, int64_t block_table_stride, int64_t weights_stride,
                             int64_t logits_stride, int max_context_len, int num_sms, int logits_dtype, int weights_dtype, void* stream);
 
+/* Hyper-connection pre-norm GEMM (reference csrc/apis/hyperconnection.hpp: tf32_hc_prenorm_gemm).  a [m, k] BF16 and b [n, k] FP32,
+ * K-major, row strides a_stride / b_stride elements; n % 8 == 0, n <= 32, k % 64 == 0, n, k > 0.  K is cut into blocks of 64, and split
+ * s of S gets (k / 64) / S blocks, the first (k / 64) % S splits one more (the reference's partition; a split without blocks is zeros):
+ *   d[s][i][j] = sum over the split's K of a[i][kk] * b[j][kk]      sqr_sum[s][i] = sum over the split's K of a[i][kk]^2
+ * num_splits = S > 0: d at d + s * d_stride_split + i * d_stride_m + j, sqr_sum [S, m] contiguous.  num_splits = 0 (the reference's None):
+ * the whole K, d [m, n] (row stride d_stride_m) and sqr_sum [m]; the call may cut K internally, writing FP32 partials to workspace
+ * (dg_split_k_workspace_bytes() bytes, NULL: no cut) and summing them in order with a second launch.  Each FP32 b is split into two BF16
+ * terms (b_hi = bf16(b), b_lo = bf16(b - b_hi)) multiplied exactly and accumulated in FP32; non-finite b is outside the contract.
+ * Every element of d and sqr_sum is written; results are bitwise repeatable for a given shape, workspace and CU count.  m == 0: nothing. */
+int dg_tf32_hc_prenorm_gemm(const void* a, const float* b, float* d, float* sqr_sum, int m, int n, int k, int64_t a_stride,
+                            int64_t b_stride, int64_t d_stride_m, int64_t d_stride_split, int num_splits, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+/* K pieces the launch above would use: num_splits if given, else its internal cut (1: none) for a workspace of workspace_bytes bytes
+ * (0: none).  Respects dg_set_num_cus; nothing is launched. */
+int dg_hc_prenorm_pieces(int m, int n, int k, int num_splits, int64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

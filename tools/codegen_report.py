@@ -171,7 +171,7 @@ def report():
                     break
         loop = body[mfma[0]:end + 1] if mfma else []
         # readable name without a demangler: _ZN2dg22dg_fp8_gemm_duo_kernelILi256ELi256ELi2ELi4ELi0EEEvNS_10GemmParamsE
-        m = re.match(r'_ZN2dg(?:3mqa)?\d+(\w+?)(?:I(.*?)EEv|Ev)', name)
+        m = re.match(r'_ZN2dg(?:3mqa|2hc)?\d+(\w+?)(?:I(.*?)EEv|Ev)', name)
         pretty = name if not m else m.group(1) + ('<' + ','.join(re.findall(r'L[ib](\d+)E', m.group(2))) + '>' if m.group(2) else '')
         out.append({'kernel': pretty, 'symbol': name, **meta[name],
                     'mfma_range_instructions': len(loop),
